@@ -14,11 +14,19 @@ chunk + 8 B per document of descriptors (the chunk / document tables are expande
 SHA-256 of every chunk, header parse, causal queue, column decode, merge (sort / RGA / succ),
 canonical re-encode, checksum, the patch Backend.applyChanges returns (wire form of am_patch.h),
 compaction, and D2H of the merged documents, patches and per-document summaries. Copies of batch
-k+1 / k-1 overlap the kernels of batch k. This is `value`. The same chain with the inputs already in
-HBM (am_pipe_run_resident) is reported beside it as `hbm_resident` and is never `value`.
+k+1 / k-1 overlap the kernels of batch k. This is `value`.
 Materializing the patches as JS objects is the host's job and is not timed here (tools/).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--docs D] [--batch B] [--slots S]
+A plain run sets up, warms up, times the steps and prints the result line. --full adds everything
+else the benchmark measures or checks, after the timed steps: the same chain with the inputs
+already in HBM (am_pipe_run_resident; reported as `hbm_resident`, never `value`), the host link's
+plain copy rates, the oracle spot check of --check documents, the digests of every merged document
+and every patch against the oracle's pinned ones (a mismatch fails the run), the decode GB/s
+figures and the CPU baselines.
+
+--dump-outputs DIR writes what the last timed step brought home (see dump_outputs) as DIR/*.npy.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--docs D] [--batch B] [--slots S] [--full] [--dump-outputs DIR]
   python bench.py --mode resident [--workload c4|c2] --docs D   # value = the HBM-resident chain (not the contract)
 """
 import argparse
@@ -253,6 +261,64 @@ def cpu_reference():
         return None
 
 
+def doc_checksums(summ_b, outs_b):
+    """Container checksum (bytes 4..8 of the merged chunk, little endian) of every document, 0 for a
+    failed one, in document order."""
+    chk = []
+    for s_, po in zip(summ_b, outs_b):
+        off = s_["out_off"].astype(np.int64)
+        ok_ = s_["status"] == 0
+        offs = np.where(ok_, off, 0)
+        b4 = [po[offs + j].astype(np.uint64) if len(po) else np.zeros(len(offs), np.uint64) for j in range(4, 8)]
+        chk.append(np.where(ok_, b4[0] | (b4[1] << 8) | (b4[2] << 16) | (b4[3] << 24), 0))
+    return np.concatenate(chk).astype(np.uint64)
+
+
+DUMP_TABLE_DOCS = 1 << 20  # documents of summary.npy (4 float64 each: 32 MiB)
+DUMP_BYTES_DOCS = 2048     # documents of documents.npy / patches.npy
+DUMP_BYTES_CAP = 8 << 20   # bytes of each of the two (float32)
+
+
+def dump_outputs(path, suffix, summ_b, outs_b, pats_b, chk):
+    """Writes what the timed path's last step brought home, as a caller of it receives it (per
+    document: summary, merged chunk, patch log), at most 50 MiB in all:
+      summary.npy    float64 [T, 4]: status, out_len, patch_len and container checksum (doc_checksums)
+                     of T = min(D, 2^20) documents
+      documents.npy  float32 [S, W]: the merged chunks of S = min(D, 2048) documents, one byte per
+                     element, rows padded with -1 (W: the longest of them, at most 8 MiB / 4 / S)
+      patches.npy    float32 [S, Wp]: their patch logs (wire form), likewise
+    Both document samples are fixed (seed 0, sorted), or every document when there are no more.
+    Offsets into the output arenas are not written: they are the engine's layout, not its result."""
+    summ = np.concatenate(summ_b)
+    D = len(summ)
+    starts = np.cumsum([0] + [len(s_) for s_ in summ_b])
+    rng = np.random.default_rng(0)
+
+    def pick(n):
+        return np.arange(D) if D <= n else np.sort(rng.choice(D, n, replace=False))
+
+    t = pick(DUMP_TABLE_DOCS)
+    table = np.stack([summ["status"][t], summ["out_len"][t], summ["patch_len"][t], chk[t]], axis=1).astype(np.float64)
+    s = pick(DUMP_BYTES_DOCS)
+
+    def rows(bufs, off_f, len_f):
+        ok = summ["status"][s] == 0
+        ln = np.where(ok, summ[len_f][s], 0).astype(np.int64)
+        w = int(min(ln.max() if len(ln) else 0, DUMP_BYTES_CAP // 4 // max(len(s), 1)))
+        out = np.full((len(s), w), -1.0, np.float32)
+        for r, i in enumerate(s.tolist()):
+            k = int(np.searchsorted(starts, i, side="right") - 1)
+            o = int(summ_b[k][off_f][i - starts[k]])
+            n = min(int(ln[r]), w)
+            out[r, :n] = bufs[k][o:o + n]
+        return out
+
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("summary", table), ("documents", rows(outs_b, "out_off", "out_len")),
+                      ("patches", rows(pats_b, "patch_off", "patch_len"))):
+        np.save(os.path.join(path, name + suffix + ".npy"), arr)
+
+
 def split_batches(arena, chunks, docs, batch):
     """Per-batch (arena slice, rebased chunk descriptors, rebased document descriptors)."""
     import numpy as np
@@ -281,13 +347,20 @@ def main():
     ap.add_argument("--slots", type=int, default=3, help="batches in flight")
     ap.add_argument("--mode", choices=["pipe", "resident"], default="pipe",
                     help="pipe: from host memory back to host memory (the `value`); resident: inputs in HBM")
-    ap.add_argument("--no-resident", action="store_true", help="pipe mode: skip the HBM-resident run reported beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the HBM-resident run, the host link's copy rates, the oracle spot "
+                         "check, the pinned digests, the decode figures and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step brought home as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-resident", action="store_true", help="--full, pipe mode: skip the HBM-resident run reported beside it")
     ap.add_argument("--full-desc", action="store_true", help="pipe mode: send full chunk / document descriptors")
     ap.add_argument("--workload", choices=["c4", "c2"], default="c4")
     ap.add_argument("--no-patch", action="store_true", help="merge without the applyChanges patch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--check", type=int, default=32, help="documents verified against the oracle (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--check", type=int, default=32, help="--full: documents verified against the oracle (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -298,7 +371,7 @@ def main():
     numa = bind_numa(local)
     # the CPU baseline's workers are forked now, before torch is imported or the GPU is touched
     procs = min(16, os.cpu_count() or 1)  # the GPU box's CPU share is 16 per GPU
-    pool = cpu_pool(procs) if rank == 0 and not args.no_cpu_baseline else None
+    pool = cpu_pool(procs) if args.full and rank == 0 and not args.no_cpu_baseline else None
     backend = os.environ.get("AM_DIST_BACKEND", "nccl")
     import numpy as np
     import torch
@@ -391,6 +464,10 @@ def main():
             step()
         pl.drain(nb * warmup)
         pl.times()
+        if args.dump_outputs:
+            # what is dumped was written by a timed step: a summary the warm-up left reads as failed
+            for sb, _, _, _ in pin_out:
+                sb.u8[:] = 0xFF
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -476,15 +553,18 @@ def main():
         extra["kernel_ms_per_step"] = ms_comp
         h2d = in_b + desc_b
         d2h = out_bytes + patch_bytes + D * pipe.SUMMARY_DT.itemsize
-        rates = pcie_rates()
         e_h2d, e_home = pl.engines()
         extra["host_link"] = {
             "bytes_per_step_rank0": {"h2d": h2d, "d2h": d2h, "descriptors": desc_b,
                                      "packed_batches": sum(k is not None for k in packed)},
-            "GBps_alone": rates, "sdma_engine_mask": {"h2d": e_h2d, "home": e_home},
-            "h2d_ms": h2d / (rates["h2d"] * 1e9) * 1e3, "d2h_ms": d2h / (rates["d2h"] * 1e9) * 1e3,
-            "ms_per_step_over_max_h2d_kernels": (elapsed * 1000.0 / args.steps) / max(h2d / (rates["h2d"] * 1e9) * 1e3, ms_comp)}
-        if not args.no_resident:
+            "sdma_engine_mask": {"h2d": e_h2d, "home": e_home}}
+        if args.full:
+            rates = pcie_rates()
+            extra["host_link"].update({
+                "GBps_alone": rates,
+                "h2d_ms": h2d / (rates["h2d"] * 1e9) * 1e3, "d2h_ms": d2h / (rates["d2h"] * 1e9) * 1e3,
+                "ms_per_step_over_max_h2d_kernels": (elapsed * 1000.0 / args.steps) / max(h2d / (rates["h2d"] * 1e9) * 1e3, ms_comp)})
+        if args.full and not args.no_resident:
             el_r, _, _, _, tot_r, msc_r, msd_r = run_resident(max(2, args.steps), 1)
             sr = max(2, args.steps)
             extra["hbm_resident"] = {
@@ -500,15 +580,11 @@ def main():
     statuses = summ_all["status"]
     alg_launch = (in_b + out_bytes + patch_bytes) / nb
     workspace = int(ws_slot)  # what one pipeline slot holds (plans + overflow room)
+    chk = doc_checksums(summ_b, outs_b) if args.full or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "" if world == 1 else "_rank%d" % rank, summ_b, outs_b, pats_b, chk)
     # per-shard digest: container checksum, length and status of every merged document
-    chk = []
-    for s_, po in zip(summ_b, outs_b):
-        off = s_["out_off"].astype(np.int64)
-        ok_ = s_["status"] == 0
-        offs = np.where(ok_, off, 0)
-        b4 = [po[offs + j].astype(np.uint64) if len(po) else np.zeros(len(offs), np.uint64) for j in range(4, 8)]
-        chk.append(np.where(ok_, b4[0] | (b4[1] << 8) | (b4[2] << 16) | (b4[3] << 24), 0))
-    digest = shard.doc_digest_np(ids, statuses, summ_all["out_len"], np.concatenate(chk).astype(np.uint64))
+    digest = shard.doc_digest_np(ids, statuses, summ_all["out_len"], chk) if args.full else None
 
     def check(i):
         k = int(np.searchsorted(starts, i, side="right") - 1)
@@ -520,7 +596,7 @@ def main():
     nerr = int((statuses != 0).sum())
     # every document's patch, materialized after the timed region (the reference's patch objects)
     t_pd = time.perf_counter()
-    pdig = patch_digest(pool, ids, summ_b, pats_b) if not args.no_patch else 0
+    pdig = patch_digest(pool, ids, summ_b, pats_b) if args.full and not args.no_patch else 0
     t_pd = time.perf_counter() - t_pd
     tot, _ = shard.exchange(dist, [D, ops_rank, nerr, out_bytes, digest or 0, pdig], xdev)
     if dist is not None:  # rank -> GPU -> NUMA node of every rank, for the line (outside the timed region)
@@ -529,7 +605,7 @@ def main():
         dist_info["numa"] = allnuma
     # correctness spot check against the oracle (outside the timed region): merged bytes and patch
     checked = 0
-    if args.check and rank == 0:
+    if args.full and args.check and rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_ffi as O
         from automerge_amd import patch as P
@@ -556,7 +632,7 @@ def main():
     value = tot[1] / (elapsed / args.steps)
     achieved = alg_launch / (t_doc * 1e-3) / 1e9 if t_doc else None
     tr = measured_traffic(extra.get("batch_docs")) if args.workload == "c4" and not args.no_patch else None
-    if t_doc:
+    if args.full and t_doc:
         # decode GB/s: algorithmic decode bytes of one launch (encoded input read + SoA
         # written, per document from an oracle-decoded sample) / the document kernel's time; the
         # kernel does the merge, encode and patch in the same time, so this is a lower bound
@@ -570,7 +646,7 @@ def main():
     cpu = cpu_baseline(pool, procs, args.workload, ops_per_doc=per_doc) if pool is not None else None
     # the whole job against the oracle's digest of every document (tests/golden/c4_digest.json)
     want = pinned_digest(tot[0]) if args.workload == "c4" and digest is not None else None
-    want_p = pinned_digest(tot[0], "patch_digest") if args.workload == "c4" and not args.no_patch else None
+    want_p = pinned_digest(tot[0], "patch_digest") if args.full and args.workload == "c4" and not args.no_patch else None
     if want is not None:
         extra["digest_pinned"] = {"expected": want, "match": tot[4] == want,
                                   "how": "oracle load + applyChanges + save of all %d documents (tools/pin_c4_digest.py)" % tot[0]}
@@ -598,12 +674,14 @@ def main():
                      "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS if achieved else None,
                      "traffic": tr["traffic_bytes"] if tr else None, "alg_bytes_per_launch": alg_launch, "avg_ms": t_doc,
                      "limiter": "VALU issue of the one-wave-per-document merge (DESIGN.md 4); not HBM"},
-        "errors": tot[2], "verified_docs": checked, "input_bytes_rank0": in_b, "output_bytes_rank0": out_bytes,
+        "errors": tot[2], "full": args.full, "input_bytes_rank0": in_b, "output_bytes_rank0": out_bytes,
         "patch_bytes_rank0": patch_bytes, "workspace_bytes_per_batch": workspace,
         "workspace_bytes_per_doc": workspace / max(1, ncap), "gen_s": t_gen,
-        "docs_per_sec": tot[0] / (elapsed / args.steps), "digest": tot[4], "patch_digest": tot[5],
-        "cpu_baseline": cpu, "cpu_reference_node": cpu_reference(),
+        "docs_per_sec": tot[0] / (elapsed / args.steps),
     }
+    if args.full:
+        line.update({"verified_docs": checked, "digest": tot[4], "patch_digest": tot[5],
+                     "cpu_baseline": cpu, "cpu_reference_node": cpu_reference()})
     line.update(extra)
     print(json.dumps(line))
     if dist is not None:

@@ -26,7 +26,7 @@ def _run(cmd, extra_env):
 
 
 def test_two_ranks_equal_one_rank():
-    args = ["bench.py", "--docs", str(DOCS), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--check", "4"]
+    args = ["bench.py", "--docs", str(DOCS), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--check", "4"]
     one = _run([sys.executable] + args, {})
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", "29517"] + args,
@@ -47,7 +47,7 @@ def test_nccl_branch_on_one_rank():
     """bench.py's RCCL path (init_process_group('nccl') bound to the device, the digest all-gather of
     device tensors, the NUMA report's all_gather_object) on one rank of one GPU: the driver's
     multi-GPU run takes this branch with N ranks."""
-    args = ["bench.py", "--docs", str(DOCS), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--check", "4"]
+    args = ["bench.py", "--docs", str(DOCS), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--check", "4"]
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
               "--master-addr", "127.0.0.1", "--master-port", "29519"] + args, {"AM_DIST_FORCE": "1"})
     rec = json.load(open(os.path.join(ROOT, "tests", "golden", "c4_digest.json")))[str(DOCS)]
