@@ -21,6 +21,7 @@ assert RESULT_DT.itemsize == C.sizeof(N.DocResult)
 
 WANT_PATCH = 2  # AM_DOC_WANT_PATCH: also write the getPatch() log of the merged document
 WANT_DIFF = 4   # AM_DOC_WANT_DIFF: also write the patch applyChanges returns
+PATCH_ROOM = 16  # AM_DOC_PATCH_ROOM: 8x the applyChanges-patch pools (a rerun after patch.U_CAPACITY)
 
 
 def pack(docs, device=0, flags=0):

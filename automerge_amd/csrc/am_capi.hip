@@ -2462,6 +2462,17 @@ void am_stage_doc_chunks(am_engine* e, size_t n, const uint8_t* const* data, con
     if (E[i].code) to_c(E[i], err_of(i));
 }
 std::string am_message_for(uint32_t code, int64_t a0, int64_t a1, const std::string& actor) { return message_for(code, a0, a1, actor); }
+// Test entry: the text of a status code without arguments (tests/test_gpu_coldec.py compares it with
+// the reference's recorded error messages). Returns the text's length; dst gets at most cap - 1 bytes.
+extern "C" size_t amx_status_message(uint32_t code, char* dst, size_t cap) {
+  const std::string m = message_for(code, 0, 0, "");
+  if (cap) {
+    const size_t k = m.size() < cap - 1 ? m.size() : cap - 1;
+    std::memcpy(dst, m.data(), k);
+    dst[k] = 0;
+  }
+  return m.size();
+}
 
 extern "C" am_doc* am_doc_init(am_engine* eng) {
   am_doc* d = new am_doc();

@@ -940,7 +940,9 @@ struct Diff {
       DCs& c = w.cs[w.cm[q].state];
       const uint32_t t15 = (uint32_t)(tag & 15);
       int64_t iv;
-      if (tag < 16 || !(t15 == 3 || t15 == 4 || t15 == 8 || t15 == 9) || !s.value_int((uint32_t)row, t15 == 3, iv)) {
+      if (tag >= 0 && tag <= 2) {
+        iv = tag == 2;  // null and false add 0, true adds 1 (JS number conversion, new.js:958)
+      } else if (tag < 16 || !(t15 == 3 || t15 == 4 || t15 == 8 || t15 == 9) || !s.value_int((uint32_t)row, t15 == 3, iv)) {
         // JS adds it as it is (a float, or a string concatenation, new.js:958): the replay goes on --
         // objectMeta does not depend on the value -- and the call reports PATCH_U_INC_VALUE at the end
         inc_nonint = true;

@@ -1306,7 +1306,7 @@ __device__ __forceinline__ bool fast_getpatch(const uint8_t* IN, uint8_t* PS, ui
   const uint64_t gm = __ballot(gfirst) & le;
   const uint32_t gs = gm ? 63u - (uint32_t)__clzll(gm) : 0u;
   const uint64_t hm = __ballot(have);
-  const uint64_t before_l = le & ~(l == 63 ? 0ull : (1ull << l)) & ~((1ull << gs) - 1);  // positions [gs, l)
+  const uint64_t before_l = le & ~(1ull << l) & ~((1ull << gs) - 1);  // positions [gs, l)
   const bool emit_key = have && (hm & before_l) == 0;
   // list elements: visible ones are inserts at their visible index
   const bool vis = child && reach && sc == 0;
@@ -1318,7 +1318,7 @@ __device__ __forceinline__ bool fast_getpatch(const uint8_t* IN, uint8_t* PS, ui
     pbad |= dtc == 100;  // datatype 0 (falsy): appendEdit's chain rule differs; k_doc writes it
   }
   const uint64_t vm = __ballot(vis);
-  const uint64_t ob = le & ~(l == 63 ? 0ull : (1ull << l)) & ~((1ull << ostart) - 1);  // positions [ostart, l)
+  const uint64_t ob = le & ~(1ull << l) & ~((1ull << ostart) - 1);  // positions [ostart, l)
   const int64_t idx = __popcll(vm & ob);
   const uint64_t pvm = vm & ob;
   const uint32_t prv = pvm ? 63u - (uint32_t)__clzll(pvm) : 0u;

@@ -1453,6 +1453,140 @@ extern "C" int amx_wave_selftest(const uint64_t* in_host, uint64_t* out_host) {
   return rc;
 }
 
+// Self-test of the lane column decoder (ColDec, am_dev_util.h) and of the LEB128 readers on the
+// device (tests/test_gpu_coldec.py checks them against the vectors recorded from the reference).
+// The streams are untrusted bytes: every read goes through Rd / WinCur, which are bounded by the
+// stream's length, and every write is bounded by maxn.
+namespace {
+struct TestBuf {
+  void* p = nullptr;
+  bool alloc(size_t n) { return hipMalloc(&p, n ? n : 1) == hipSuccess; }
+  bool up(const void* src, size_t n) { return n == 0 || hipMemcpy(p, src, n, hipMemcpyHostToDevice) == hipSuccess; }
+  bool down(void* dst, size_t n) const { return n == 0 || hipMemcpy(dst, p, n, hipMemcpyDeviceToHost) == hipSuccess; }
+  template <typename T> T* as() const { return static_cast<T*>(p); }
+  ~TestBuf() { if (p) (void)hipFree(p); }
+};
+// offs[0..n] ascending and inside [0, nbytes]
+bool offsets_ok(const uint64_t* offs, uint32_t n, uint64_t nbytes) {
+  for (uint32_t i = 0; i < n; i++) if (offs[i] > offs[i + 1]) return false;
+  return offs[n] <= nbytes;
+}
+}  // namespace
+
+// One lane per stream: cd_init, then cd_next_* of the stream's DT_* type until cd_done, maxn values
+// or the first non-zero status. vals: the integer (AM_NULL64 = null), 0/1 for booleans, the byte
+// offset inside the stream for strings; lens: string length (AM_NOSTR = null), 0 otherwise.
+__global__ void __launch_bounds__(64) k_coldec_selftest(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offs,
+                                                        const uint8_t* __restrict__ types, uint32_t nstreams, uint32_t maxn,
+                                                        uint32_t* __restrict__ status, uint32_t* __restrict__ count,
+                                                        int64_t* __restrict__ vals, uint32_t* __restrict__ lens) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= nstreams) return;
+  const uint8_t type = types[i];
+  uint32_t st = AM_OK, n = 0;
+  if (type > DT_BOOL) {
+    st = AM_U_VALUE;
+  } else {
+    ColDec d;
+    cd_init(d, type, bytes + offs[i], offs[i + 1] - offs[i]);
+    int64_t* v = vals + (uint64_t)i * maxn;
+    uint32_t* l = lens + (uint64_t)i * maxn;
+    while (n < maxn && !cd_done(d)) {
+      int64_t x = 0;
+      uint32_t len = 0;
+      if (type == DT_UTF8) {
+        uint64_t off;
+        st = cd_next_str(d, off, len);
+        x = (int64_t)off;
+      } else if (type == DT_DELTA) {
+        st = cd_next_delta(d, x);
+      } else if (type == DT_BOOL) {
+        bool b = false;
+        st = cd_next_bool(d, b);
+        x = b ? 1 : 0;
+      } else {
+        st = cd_next_int(d, x);
+      }
+      if (st) break;
+      v[n] = x;
+      l[n] = len;
+      n++;
+    }
+  }
+  status[i] = st;
+  count[i] = n;
+}
+extern "C" int amx_coldec_selftest(const uint8_t* bytes, uint64_t nbytes, const uint64_t* offs, const uint8_t* types,
+                                   uint32_t nstreams, uint32_t maxn, uint32_t* status, uint32_t* count, int64_t* vals,
+                                   uint32_t* lens) {
+  if (nstreams == 0) return 0;
+  if (maxn == 0 || !offsets_ok(offs, nstreams, nbytes)) return 2;
+  const size_t nv = (size_t)nstreams * maxn;
+  TestBuf db, doff, dty, dst, dcnt, dval, dlen;
+  if (!db.alloc(nbytes) || !doff.alloc((nstreams + 1) * 8ull) || !dty.alloc(nstreams) || !dst.alloc(nstreams * 4ull) ||
+      !dcnt.alloc(nstreams * 4ull) || !dval.alloc(nv * 8) || !dlen.alloc(nv * 4))
+    return 1;
+  if (!db.up(bytes, nbytes) || !doff.up(offs, (nstreams + 1) * 8ull) || !dty.up(types, nstreams)) return 1;
+  if (hipMemset(dval.p, 0, nv * 8) != hipSuccess || hipMemset(dlen.p, 0, nv * 4) != hipSuccess) return 1;
+  hipLaunchKernelGGL(k_coldec_selftest, dim3((nstreams + 63) / 64), dim3(64), 0, 0, db.as<uint8_t>(), doff.as<uint64_t>(),
+                     dty.as<uint8_t>(), nstreams, maxn, dst.as<uint32_t>(), dcnt.as<uint32_t>(), dval.as<int64_t>(),
+                     dlen.as<uint32_t>());
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 1;
+  return !(dst.down(status, nstreams * 4ull) && dcnt.down(count, nstreams * 4ull) && dval.down(vals, nv * 8) &&
+           dlen.down(lens, nv * 4));
+}
+
+// The LEB128 readers, one lane per vector. fn: 0 rd_u53, 1 rd_i53, 2 leb_u64, 3 leb_i64 (am_dev_util.h),
+// 4 win_leb_u64, 5 win_leb_i64, 6 win_u53, 7 win_i53 (the line reader of k_chunks, over the same bytes).
+// Per vector: status, end offset, and the value as its high and low 32-bit words.
+__global__ void __launch_bounds__(64) k_leb_selftest(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offs,
+                                                     const uint8_t* __restrict__ fns, uint32_t n, uint32_t* __restrict__ status,
+                                                     uint32_t* __restrict__ end, uint32_t* __restrict__ hi, uint32_t* __restrict__ lo) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t len = offs[i + 1] - offs[i];
+  Rd r{bytes + offs[i], len, 0};
+  LineRd w{bytes, offs[i], ~0ull, make_uint4(0, 0, 0, 0)};
+  WinCur c{0, len};
+  uint32_t st = AM_OK, h = 0, l = 0;
+  int32_t sh = 0;
+  int64_t v = 0;
+  const uint8_t fn = fns[i];
+  switch (fn) {
+    case 0: st = rd_u53(r, v); break;
+    case 1: st = rd_i53(r, v); break;
+    case 2: st = leb_u64(r, h, l); break;
+    case 3: st = leb_i64(r, sh, l); h = (uint32_t)sh; break;
+    case 4: st = win_leb_u64(w, c, h, l); break;
+    case 5: st = win_leb_i64(w, c, sh, l); h = (uint32_t)sh; break;
+    case 6: st = win_u53(w, c, v); break;
+    case 7: st = win_i53(w, c, v); break;
+    default: st = AM_U_VALUE; break;
+  }
+  if (fn < 2 || fn == 6 || fn == 7) { h = (uint32_t)((uint64_t)v >> 32); l = (uint32_t)v; }
+  status[i] = st;
+  end[i] = (uint32_t)(fn >= 4 ? c.off : r.off);
+  hi[i] = st ? 0 : h;
+  lo[i] = st ? 0 : l;
+}
+extern "C" int amx_leb_selftest(const uint8_t* bytes, uint64_t nbytes, const uint64_t* offs, const uint8_t* fns, uint32_t n,
+                                uint32_t* status, uint32_t* end, uint32_t* hi, uint32_t* lo) {
+  if (n == 0) return 0;
+  if (!offsets_ok(offs, n, nbytes)) return 2;
+  // the line reader loads whole aligned 16-byte lines: zeroed slack after the last stream
+  const size_t cap = ((size_t)nbytes + 15) / 16 * 16 + 16;
+  TestBuf db, doff, dfn, dst, dend, dhi, dlo;
+  if (!db.alloc(cap) || !doff.alloc((n + 1) * 8ull) || !dfn.alloc(n) || !dst.alloc(n * 4ull) || !dend.alloc(n * 4ull) ||
+      !dhi.alloc(n * 4ull) || !dlo.alloc(n * 4ull))
+    return 1;
+  if (hipMemset(db.p, 0, cap) != hipSuccess) return 1;
+  if (!db.up(bytes, nbytes) || !doff.up(offs, (n + 1) * 8ull) || !dfn.up(fns, n)) return 1;
+  hipLaunchKernelGGL(k_leb_selftest, dim3((n + 63) / 64), dim3(64), 0, 0, db.as<uint8_t>(), doff.as<uint64_t>(), dfn.as<uint8_t>(),
+                     n, dst.as<uint32_t>(), dend.as<uint32_t>(), dhi.as<uint32_t>(), dlo.as<uint32_t>());
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 1;
+  return !(dst.down(status, n * 4ull) && dend.down(end, n * 4ull) && dhi.down(hi, n * 4ull) && dlo.down(lo, n * 4ull));
+}
+
 #ifdef AM_PHASE_CLOCK
 extern "C" int amx_phase_cycles(unsigned long long* out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(am_phase_cycles), sizeof(unsigned long long) * 48) != hipSuccess) return -1;

@@ -544,7 +544,9 @@ AM_PHD inline bool patch_scan(const Src& src, PatchOut& o, PatchScratch& w, int6
       const int32_t st = w.cm_state[q];
       const uint32_t t15 = (uint32_t)(tag & 15);
       int64_t iv;
-      if (tag < 16 || !(t15 == 3 || t15 == 4 || t15 == 8 || t15 == 9) || !src.value_int(i, t15 == 3, iv)) {
+      if (tag >= 0 && tag <= 2) {
+        iv = tag == 2;  // null and false add 0, true adds 1 (JS number conversion, new.js:958)
+      } else if (tag < 16 || !(t15 == 3 || t15 == 4 || t15 == 8 || t15 == 9) || !src.value_int(i, t15 == 3, iv)) {
         o.status = PATCH_U_VALUE;  // non-integer increment (JS would concatenate / add a float)
         return false;
       }

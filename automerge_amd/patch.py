@@ -13,6 +13,7 @@ HDR_DT = np.dtype([("magic", "<u4"), ("status", "<u4"), ("arg0", "<i8"), ("arg1"
                    ("nbytes", "<u8"), ("meta_bytes", "<u8")])
 assert HDR_DT.itemsize == 48
 MAGIC = 0x32504D41
+U_CAPACITY = 106  # header status AM_U_CAPACITY: the patch pools were too small (rerun with batch.PATCH_ROOM)
 
 PR_ACTOR, PR_CLOCK, PR_OBJ, PR_KEY, PR_PROP, PR_INSERT, PR_MULTI, PR_UPDATE, PR_REMOVE = range(1, 10)
 (PV_NULL, PV_FALSE, PV_TRUE, PV_STR, PV_UINT, PV_INT, PV_F64, PV_COUNTER, PV_TIMESTAMP, PV_BYTES,

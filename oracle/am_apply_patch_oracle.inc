@@ -229,9 +229,7 @@ static void update_patch_property(ctx_t *c, apatch *ap, int64_t obj_ctr, int64_t
       fail(c, "increment operation %lld@%s for unknown counter", (long long)id_ctr, a);
     }
     cstate *cs = &s->cs[s->map[q].state];
-    vclass k = value_class(c, op);
-    if (k.ty != TY_NUMBER) unsupported(c, "non-numeric counter increment");
-    cs->value += value_int(c, op);
+    cs->value += inc_amount(c, op);
     cs->nleft--; /* delete counterState.succs[opId] (the map entry itself stays, new.js:959) */
     if (cs->nleft == 0) { pv.kind = PV_COUNTER; pv.counter = cs->value; pk_ctr = cs->op_ctr; pk_actor = cs->op_actor; }
   } else if (!overwritten) {

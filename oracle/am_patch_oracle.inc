@@ -84,6 +84,14 @@ static int64_t value_int(ctx_t *c, const op_t *op) {
   if (tag % 16 == 3) return rd_u53(c, &d);
   return rd_i53(c, &d);
 }
+/* counterState.value += decodeValue(...).value (new.js:958): null and false add 0, true adds 1 */
+static int64_t inc_amount(ctx_t *c, const op_t *op) {
+  const int64_t tag = op->val_len.null ? 0 : op->val_len.v;
+  if (tag == 0 || tag == 1) return 0;
+  if (tag == 2) return 1;
+  if (value_class(c, op).ty != TY_NUMBER) unsupported(c, "non-numeric counter increment");
+  return value_int(c, op);
+}
 
 /* ---- JSON output ---- */
 static void js_raw(ctx_t *c, bbuf *o, const char *s) { bb_raw(c, o, (const uint8_t *)s, strlen(s)); }
@@ -408,9 +416,7 @@ static pnode *document_patch(ctx_t *c, const docst_t *st, int64_t *max_op) {
         fail(c, "increment operation %lld@%s for unknown counter", (long long)id_ctr, a);
       }
       cstate *cs = &ps.cs[ps.map[q].state];
-      vclass k = value_class(c, op);
-      if (k.ty != TY_NUMBER) unsupported(c, "non-numeric counter increment");
-      cs->value += value_int(c, op);
+      cs->value += inc_amount(c, op);
       /* delete counterState.succs[opId]: op ids are unique, so each successor is consumed once */
       cs->nleft--;
       if (cs->nleft == 0) {
